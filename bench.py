@@ -21,6 +21,7 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                    frac_of_2500, the dominant kernel, and where each gradient bucket's all-reduce was issued (--train-leg 0 = off);
   "cpu_baseline" - the torch-CPU oracle (a port of the reference path, pinned to it by golden vectors)
                    timed on this box's host cores on a bounded sample of the same workload.
+--dump-outputs DIR also writes what the last timed step returned (DIR/<name>.npy) to compare two builds output for output.
 """
 import argparse
 import ctypes
@@ -72,6 +73,35 @@ def step(model, t):
     return model(t["roi_img"], roi_classes=t["roi_cls"], roi_coord_2d=t["roi_coord_2d"], roi_cams=t["roi_cam"],
                  roi_centers=t["roi_center"], roi_whs=t["roi_wh"], roi_extents=t["roi_extent"],
                  resize_ratios=t["resize_ratio"], do_loss=False, fps=t["fps"])
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(outs, out_dir, batch, what):
+    """`--dump-outputs DIR`: the arrays one call of the timed path returned, as DIR/<name>.npy - floating outputs in float32 (float64
+    stays float64), integer / boolean ones in float64 (exact).  At most DUMP_LIMIT_BYTES in all: past that, the same fixed seeded
+    sample of the crops (leading dimension `batch`) is taken from every per-crop array and its indices are written as crop_index.npy."""
+    arrs = {}
+    for k, v in outs.items():
+        if v is None:
+            continue
+        a = v.detach().cpu()
+        a = a.double() if (not a.is_floating_point() or a.dtype == torch.float64) else a.float()
+        arrs[k] = a.numpy()
+    per_crop = sum(a.nbytes // batch for a in arrs.values() if a.ndim and a.shape[0] == batch)
+    fixed = sum(a.nbytes for a in arrs.values() if not (a.ndim and a.shape[0] == batch))
+    slack = 128 * (len(arrs) + 1) + 8 * batch  # .npy headers, crop_index.npy
+    if fixed + per_crop * batch + slack > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - fixed - slack) // max(per_crop, 1))
+        idx = np.sort(np.random.default_rng(0).choice(batch, size=keep, replace=False))
+        arrs = {k: a[idx] if a.ndim and a.shape[0] == batch else a for k, a in arrs.items()}
+        arrs["crop_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    total = sum(a.nbytes for a in arrs.values())
+    print(f"[bench] {what}: {len(arrs)} arrays, {total / 1e6:.1f} MB -> {out_dir}", file=sys.stderr)
 
 
 def conv_flops(d):
@@ -320,7 +350,7 @@ def train_roofline(eng, one_step, reps=3):
 
 
 def train_leg(rank, world, device, dist, dtype="bf16", B=32, backbone=34, res=256, steps=100, warmup=3, preheat=3.0, buckets="stages",
-              comm_dtype=None):
+              comm_dtype=None, dump=None):
     """The training step (fwd + nine losses + bwd + per-stage gradient all-reduce + fused Ranger + weight re-pack) timed like the
     headline: W warm-up steps, `preheat` seconds of un-timed steps, barrier, EXACTLY `steps` steps, barrier, max over ranks.  Every rank
     runs the same number of steps (the steps carry the all-reduces).  Returns the figures as a dict (rank 0's view); `--train` prints
@@ -397,6 +427,8 @@ def train_leg(rank, world, device, dist, dtype="bf16", B=32, backbone=34, res=25
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
+    if dump and rank == 0:  # (before the event-timed steps below take the engine further)
+        dump_outputs(losses, dump, B, "losses of the last timed training step")
     el = torch.tensor([elapsed], dtype=torch.float64, device=device if dist is None or dist.get_backend() == "nccl" else "cpu")
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -433,7 +465,7 @@ def train_bench(args, rank, world, device, dist):
     RCCL).  Not the headline metric."""
     B = args.batch if args.batch != 64 else 32
     t = train_leg(rank, world, device, dist, dtype=args.dtype, B=B, backbone=args.backbone, res=args.res, steps=args.steps, warmup=args.warmup,
-                  preheat=args.preheat, buckets=args.buckets, comm_dtype=args.allreduce_dtype)
+                  preheat=args.preheat, buckets=args.buckets, comm_dtype=args.allreduce_dtype, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps({
             "metric": f"RGB-D crops/sec, TRAINING step (fwd+losses+bwd+allreduce+Ranger) at {args.res}x{args.res}", "value": t["crops_per_s"],
@@ -498,6 +530,11 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="secondary line: training step (fwd + losses + bwd + bucketed RCCL all-reduce + Ranger), B=32/GPU; "
                          "fp32, or mixed precision (cfg.SOLVER.AMP.ENABLED) with --dtype bf16")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step returned as DIR/<name>.npy (rank 0; float32, integer outputs "
+                         "as float64; at most 64 MB in all, a fixed seeded sample of the crops past that).  The inputs are seeded: with the "
+                         "same arguments two builds compare output for output.  --train: the losses of that step - the weights it ran on "
+                         "took every earlier step too, so compare training runs with --preheat 0 (a fixed number of steps)")
     args = ap.parse_args()
 
     # --gpus N is the number of ranks (one per GPU).  Launched bare (`python bench.py --gpus N`, no WORLD_SIZE in the environment) with
@@ -506,6 +543,8 @@ def main():
     # process that has initialised HIP).  Under a launcher WORLD_SIZE must equal --gpus: a mismatch is an error, not a silent 1-rank run.
     if args.gpus < 1:
         raise SystemExit(f"bench.py: --gpus {args.gpus}: need at least one rank")
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps}: need at least one timed step")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import socket
         import subprocess
@@ -577,13 +616,15 @@ def main():
             if args.trace and i % args.trace == 0:
                 marks.append(torch.cuda.Event(enable_timing=True))
                 marks[-1].record()
-            step(model, t)
+            o = step(model, t)
         if args.trace:
             marks.append(torch.cuda.Event(enable_timing=True))
             marks[-1].record()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(o, args.dump_outputs, B, "outputs of the last timed step")
     my_elapsed = elapsed
     el = torch.tensor([elapsed], dtype=torch.float64, device=device if dist is None or dist.get_backend() == "nccl" else "cpu")
     per_rank = [el.clone() for _ in range(world)]

@@ -37,3 +37,11 @@ def fps_cases():
     cases.append(("gauss_n13000_s128_center", "gauss", 13000, 128, 9, "center"))
     cases.append(("gauss_n200000_s64_center", "gauss", 200000, 64, 13, "center"))
     return cases
+
+
+def library_cases():
+    """(name, points, sn): the unit-gaussian clouds on which the C oracle is held to the reference library's init_center entry point
+    (tests/golden/fps_ref_lib_golden.npz: that library's index vectors, so the check needs no build of the reference)"""
+    rng = np.random.default_rng(0)
+    return [(f"gauss_n{n}_s{sn}_center", np.ascontiguousarray(rng.standard_normal((n, 3)), dtype=np.float32), sn)
+            for n, sn in ((257, 16), (4096, 33), (20000, 64))]

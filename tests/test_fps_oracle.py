@@ -5,9 +5,8 @@ import ctypes
 import os
 
 import numpy as np
-import pytest
 
-from tests.fps_cases import fps_cases, make_cloud
+from tests.fps_cases import fps_cases, library_cases, make_cloud
 
 P = ctypes.c_void_p
 
@@ -30,17 +29,21 @@ def test_oracle_matches_reference_golden(oracle_lib, golden_dir):
         assert np.array_equal(idx, gold[name]), name
 
 
-def test_oracle_matches_reference_library_if_present(oracle_lib):
+def test_oracle_matches_reference_library_if_present(oracle_lib, golden_dir):
+    """the reference library's init_center indices on unit-gaussian clouds: stored (fps_ref_lib_golden.npz), and also recomputed by the
+    library itself when oracle/_ref is built"""
+    gold = np.load(os.path.join(golden_dir, "fps_ref_lib_golden.npz"))
+    cases = library_cases()
+    assert sorted(gold.files) == sorted(name for name, _, _ in cases)
     ref = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "libfps_ref.so")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref not built (reference absent)")
-    lib = ctypes.CDLL(ref)
-    rng = np.random.default_rng(0)
-    for n, sn in ((257, 16), (4096, 33), (20000, 64)):
-        pts = np.ascontiguousarray(rng.standard_normal((n, 3)), dtype=np.float32)
-        want = np.zeros(sn, dtype=np.int32)
-        lib.farthest_point_sampling_init_center(pts.ctypes.data_as(P), want.ctypes.data_as(P), n, sn)
-        assert np.array_equal(_oracle(oracle_lib, pts, sn, "center"), want)
+    lib = ctypes.CDLL(ref) if os.path.exists(ref) else None
+    for name, pts, sn in cases:
+        want = gold[name]
+        if lib is not None:
+            live = np.zeros(sn, dtype=np.int32)
+            lib.farthest_point_sampling_init_center(pts.ctypes.data_as(P), live.ctypes.data_as(P), len(pts), sn)
+            assert np.array_equal(live, want), name
+        assert np.array_equal(_oracle(oracle_lib, pts, sn, "center"), want), name
 
 
 def test_edge_semantics(oracle_lib):

@@ -21,9 +21,18 @@ def test_config_base_merge_and_delete(tmp_path):
     assert cfg.A.get("nope", 4) == 4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference configs only exist in the build container")
-def test_loads_reference_config_files_unchanged():
-    cfg = Config.fromfile("/root/reference/configs/gdrn/lm/a6_cPnP_lm13.py")
+def _reference_configs(golden_dir):
+    """the reference's configs/gdrn/**.py as Config.fromfile resolved them, unchanged files (tools/oracle/gen_config_golden.py): the
+    sections MODEL / SOLVER / TEST / INPUT of the 138 files that define a model, by path relative to configs/gdrn"""
+    import gzip
+    import json
+
+    with gzip.open(os.path.join(golden_dir, "reference_configs.json.gz"), "rt") as f:
+        return {k: Config(v) for k, v in json.load(f).items()}
+
+
+def test_loads_reference_config_files_unchanged(golden_dir):
+    cfg = _reference_configs(golden_dir)["lm/a6_cPnP_lm13.py"]
     assert cfg.MODEL.CDPN.ROT_HEAD.NUM_REGIONS == 32 and cfg.MODEL.CDPN.PNP_NET.ROT_TYPE == "allo_rot6d"
     assert cfg.MODEL.CDPN.BACKBONE.NUM_LAYERS == 34 and cfg.SOLVER.OPTIMIZER_CFG.type == "Ranger"
     assert "momentum" not in cfg.SOLVER.OPTIMIZER_CFG  # _delete_=True honoured
@@ -122,24 +131,15 @@ def test_unsupported_switches_fail_loudly(path, value):
         build_model_optimizer(cfg)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs/gdrn"), reason="needs the reference checkout (build container only)")
-def test_every_shipped_rgbd_config_builds_through_the_factory(monkeypatch):
+def test_every_shipped_rgbd_config_builds_through_the_factory(monkeypatch, golden_dir):
     """all model configs under configs/gdrn (138: K = 32 / 64, MASK_ATTENTION mul / none, 30 with SOLVER.AMP) load unchanged and
     build: same 305 state_dict keys, Ranger with three parameter groups.  BASE_LR is derived from OPTIMIZER_CFG the way
     main_gdrn.py:63-74 does before it calls the factory."""
-    import glob
-
     # the shipped configs name BACKBONE.PRETRAINED = "torchvision://resnet34", which cannot be resolved offline: the factory then
     # raises unless told that a random trunk is acceptable (test_pretrained_backbone_loading covers the loading itself)
     monkeypatch.setenv("RDPN6D_ALLOW_RANDOM_BACKBONE", "1")
     n = amp = k64 = 0
-    for f in sorted(glob.glob("/root/reference/configs/gdrn/**/*.py", recursive=True)):
-        try:
-            cfg = Config.fromfile(f)
-        except ModuleNotFoundError:
-            continue  # tlessSO/icp.py imports mmcv at module level
-        if "MODEL" not in cfg:
-            continue  # empty placeholder files
+    for f, cfg in sorted(_reference_configs(golden_dir).items()):
         cfg.MODEL.DEVICE = "cpu"
         model, opt = build_model_optimizer(cfg)
         assert len(model.state_dict()) == 305 and type(opt).__name__ == "Ranger" and len(opt.param_groups) == 3, f
@@ -329,6 +329,35 @@ def test_bench_gpus_flag_is_checked_before_anything_touches_a_gpu():
         env.pop("WORLD_SIZE")
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"], env=env, cwd=root, capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and "no CPU fallback" in r.stderr
+
+
+def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 for floating outputs, float64 for integer ones, None skipped; past the size cap every per-crop
+    array keeps the same fixed seeded sample of crops, named in crop_index.npy"""
+    import bench
+
+    B = 16
+    g = torch.Generator().manual_seed(0)
+    outs = {"region": torch.randn(B, 33, 8, 8, generator=g).bfloat16(), "rot": torch.randn(B, 3, 3, generator=g),
+            "pnp_num_inliers": torch.randint(0, 4096, (B,), generator=g, dtype=torch.int32), "loss": torch.tensor(0.25, dtype=torch.float64),
+            "consistent_map": None}
+    bench.dump_outputs(outs, str(tmp_path / "all"), B, "test")
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["loss", "pnp_num_inliers", "region", "rot"]
+    assert got["region"].dtype == np.float32 and np.array_equal(got["region"], outs["region"].float().numpy())
+    assert got["pnp_num_inliers"].dtype == np.float64 and np.array_equal(got["pnp_num_inliers"], outs["pnp_num_inliers"].numpy())
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == ()
+    per_crop = (33 * 8 * 8 + 9) * 4 + 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 5 * per_crop + 2000)
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d), B, "test")
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    idx = a["crop_index"].astype(np.int64)
+    assert a["crop_index"].dtype == np.float64 and len(idx) == 5 and np.all(np.diff(idx) > 0)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    assert all(np.array_equal(a[k], b[k]) for k in a) and np.array_equal(a["rot"], got["rot"][idx]) and np.array_equal(a["region"], got["region"][idx])
+    assert np.array_equal(a["loss"], got["loss"])
 
 
 def test_fps_python_face_returns_what_the_reference_returns(oracle_lib, monkeypatch):

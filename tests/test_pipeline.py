@@ -221,3 +221,33 @@ def test_bench_default_line_carries_the_training_leg():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--preheat", "0", "--train-leg", "0",
                         "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "train" not in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def test_bench_dump_outputs_is_what_the_timed_path_returned(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the outputs of its LAST timed step: the same forward on the same seeded batch (rank 0:
+    synth.make_inputs(B, seed=100)) in this process returns them bit for bit - the inputs, and so the dump, are the same from run to
+    run; floating outputs as float32, integer ones as float64"""
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from rdpn6d_amd import synth
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 8
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--preheat", "0", "--train-leg", "0",
+                        "--no-cpu-baseline", "--batch", str(B), "--dump-outputs", str(tmp_path)], cwd=root, capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    dev = torch.device("cuda:0")
+    model, _ = bench.build_model(dev)
+    t = {k: torch.from_numpy(v).to(dev) for k, v in synth.make_inputs(B, seed=100).items()}
+    with torch.no_grad():
+        o = bench.step(model, t)
+    want = {k: v.cpu().numpy() for k, v in o.items() if v is not None}
+    assert sorted(f[:-4] for f in os.listdir(tmp_path)) == sorted(want)
+    for k, w in want.items():
+        got = np.load(os.path.join(tmp_path, f"{k}.npy"))
+        assert got.dtype == (np.float32 if np.issubdtype(w.dtype, np.floating) else np.float64), k
+        assert got.shape == w.shape and np.array_equal(got, w.astype(got.dtype)), k
